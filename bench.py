@@ -4,16 +4,21 @@ Step = RHyperLogLog.addAll(n synthetic 16-byte keys already resident in HBM)
        + (N > 1) RCCL MAX all-reduce of the 16384 registers + count().
 The keys are the SURVEY.md 8d C2 stream (splitmix64, seed 0x5EED0002), each
 rank taking its own contiguous range (weak scaling: n keys per GPU).
-Secondary fields of the same line:
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K
+steps and prints the result line; `--dump-outputs DIR` also writes what the
+last timed step returned to its caller as DIR/<name>.npy.  Everything else is
+behind `--full`, which adds these secondary fields to the same line:
   `bloom`   the C3 Bloom filter per node (1B inserts at 1% FPP, EXTENDED mode,
             sharded over the ranks and merged with the RCCL slice-OR, then 1B
             contains queries sharded over the replicated filter);
   `c4`      BASELINE configs[3] per GPU: 1B variable-length keys (+ RCCL MAX);
   `c5`, `c5_zipf`  BASELINE configs[4] per GPU: 1M sketches, 500M pairs per
             step, uniform and Zipf(1.1) groups, with count / countWith / mergeWith;
-each with its own ms_per_step, roofline and PMC traffic (--no-extra skips them).
+each with its own ms_per_step, roofline and PMC traffic (--no-extra skips them);
+  `cpu_baseline`, `pcie_inclusive`  the CPU restatement and host-resident keys;
+  `c5.checkpoint` (also `--workload c5 --full`)  the pool's export / import.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--keys N_PER_GPU]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--keys N_PER_GPU] [--dump-outputs DIR] [--full]
 """
 from __future__ import annotations
 
@@ -349,15 +354,17 @@ WORKLOADS = {
 
 
 def run_hll(ctx, wl: str, n: int, steps: int, warmup: int, zipf: float = 0.0, groups_n: int = 1_000_000,
-            batch_ops: int = 100_000, bloom_keys: int = 0):
+            batch_ops: int = 100_000, bloom_keys: int = 0, checkpoint: bool = True, want_outputs: bool = False):
     """One HLL workload (c2 / c4 / c5) on this rank: inputs generated into HBM
     (untimed), `warmup` untimed steps, then `steps` timed steps between
     barriers; the max over ranks of the elapsed time.  Returns the bench
-    fields of that workload (value, ms_per_step, roofline, ...)."""
+    fields of that workload (value, ms_per_step, roofline, ...); with
+    `want_outputs` also `outputs`: what the last timed step gave its caller."""
     engine, client, rank, world = ctx["engine"], ctx["client"], ctx["rank"], ctx["world"]
     from redisson_amd import devmem, shard
 
     extra = {}
+    last = {}
     hll = client.getHyperLogLog("bench-" + wl)
     if wl == "c2":
         keys = devmem.gen_keys16(engine, SEED_C2, rank * n, n)
@@ -420,7 +427,7 @@ def run_hll(ctx, wl: str, n: int, steps: int, warmup: int, zipf: float = 0.0, gr
             for op in ops:
                 op.wait()
             return int(counts_out[0])
-        hll.addAll(kb)
+        last["changed"] = hll.addAll(kb)
         if world > 1:
             slot = client._hll_slot("bench-" + wl, False)
             shard.hll_allreduce(slot.pool, slot.id)  # RCCL MAX over xGMI
@@ -480,6 +487,20 @@ def run_hll(ctx, wl: str, n: int, steps: int, warmup: int, zipf: float = 0.0, gr
         t = torch.tensor([elapsed], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    outputs = None
+    if want_outputs and steps > 0:
+        # untimed: the last step's replies as its caller holds them, and the
+        # sketch state that step left behind, read back through the public calls
+        import numpy as np
+
+        if wl == "c5":
+            outputs = {"counts": counts_out[:own_count if world > 1 else G].astype(np.float64),
+                       "count_with": cw_out.astype(np.float64),
+                       "merged_counts": pool.count(md).astype(np.float64)}
+        else:
+            outputs = {"count": np.array([cards[-1]], np.float64),
+                       "changed": np.array([last["changed"]], np.float64),
+                       "registers": hll.registers().astype(np.float32)}
 
     value = n * world * steps / elapsed
     avg_launch_s = (add_ms / 1e3) / max(1, add_launches)
@@ -532,7 +553,7 @@ def run_hll(ctx, wl: str, n: int, steps: int, warmup: int, zipf: float = 0.0, gr
         if stage_ms:
             res["roofline"]["stage_ms_per_launch"] = stage_ms
         res["add_ms_per_step"] = avg_launch_s * 1e3
-        if world == 1 and zipf == 0:
+        if checkpoint and world == 1 and zipf == 0:
             res["checkpoint"] = checkpoint_bench(engine, pool)
     for b in bufs:
         b.free()
@@ -540,7 +561,30 @@ def run_hll(ctx, wl: str, n: int, steps: int, warmup: int, zipf: float = 0.0, gr
         pool.close()
     else:
         hll.delete()
+    if outputs is not None:
+        res["outputs"] = outputs
     return res
+
+
+DUMP_BUDGET_BYTES = 64_000_000  # all of --dump-outputs together
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: each array as out_dir/<name>.npy (float32 / float64).
+    An array over its share of the budget is cut to a fixed sample of its
+    elements (indices drawn once from seed 0, in ascending order)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=share // a.itemsize))
+            a = a.ravel()[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def checkpoint_bench(engine, pool):
@@ -695,6 +739,13 @@ def main():
     # slower while the clock settles (profiles/r02_roofline_check.json)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the Bloom (C3), C4, C5 and C5-Zipf secondary "
+                         "workloads, the C5 checkpoint, the CPU baselines and the host-resident keys "
+                         "(the --no-* options below drop single legs of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned (and the sketch state it left) "
+                         "as DIR/<name>.npy; inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--workload", choices=("c2", "c4", "c5"), default="c2",
                     help="c2: 16-byte keys (headline); c4: variable-length keys; c5: grouped sketches")
     ap.add_argument("--keys", type=int, default=None,
@@ -753,7 +804,7 @@ def main():
     engine = client.engine
     if world > 1:
         shard.init_comm(engine)
-    elif not args.no_bloom and args.workload == "c2":
+    elif args.full and not args.no_bloom and args.workload == "c2":
         shard.init_comm_single(engine)  # the node-level Bloom merge runs through the same call at N = 1
     # what RCCL itself reports (ncclCommCount): every rank must have joined
     rccl_nranks, rccl_rank = shard.comm_info(engine)
@@ -763,9 +814,13 @@ def main():
     ctx = {"engine": engine, "client": client, "rank": rank, "world": world}
     wl = args.workload
     n = args.keys if args.keys is not None else (500_000_000 if wl == "c5" else 1_000_000_000)
-    bloom_on = wl == "c2" and not args.no_bloom
+    bloom_on = args.full and wl == "c2" and not args.no_bloom
     head = run_hll(ctx, wl, n, args.steps, args.warmup, zipf=args.zipf, groups_n=args.groups,
-                   batch_ops=args.batch_ops, bloom_keys=args.bloom_keys if bloom_on else 0)
+                   batch_ops=args.batch_ops, bloom_keys=args.bloom_keys if bloom_on else 0,
+                   checkpoint=args.full, want_outputs=args.dump_outputs is not None)
+    outputs = head.pop("outputs", None)
+    if outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, outputs)
     result = {
         "metric": "HLL adds/s + Bloom lookups/s (node), % HBM roofline, 1/2/4/8 MI355X",
         "value": head.pop("value"),
@@ -795,7 +850,7 @@ def main():
             ir["traffic"] = tr["bytes"]
             ir["traffic_source"] = tr["source"]
             ir["traffic_GBps"] = tr["bytes"] * ir["achieved"] / ir["algorithmic_bytes"]  # traffic / insert time
-    if wl == "c2" and not args.no_extra:
+    if args.full and wl == "c2" and not args.no_extra:
         # the other per-GPU BASELINE configs, each with its own timing and
         # roofline: C4 (configs[3] per GPU: 1B variable-length keys), C5
         # (configs[4] per GPU: 1M sketches, 500M pairs) uniform and Zipf(1.1)
@@ -805,7 +860,7 @@ def main():
             result[key] = run_hll(ctx, w2, n2, args.extra_steps, args.extra_warmup, zipf=z, groups_n=args.groups,
                                   batch_ops=args.batch_ops)
             log("%s: %.3f ms/step (%.1f s)" % (key, result[key]["ms_per_step"], time.perf_counter() - t0))
-    if rank == 0 and world == 1 and wl == "c2" and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and wl == "c2" and not args.no_cpu:
         thr = max(1, min(args.cpu_threads, os.cpu_count() or 1))
         result["cpu_baseline"] = cpu_baseline(args.cpu_sample, args.cpu_passes, thr)
         if not args.no_bloom:
