@@ -305,6 +305,48 @@ int rsk_bloom_import_bits(rsk_bloom *b, const uint8_t *buf, size_t len);
 int rsk_bloom_or_bits(rsk_bloom *b, const uint8_t *bits, size_t len, uint32_t location);
 void *rsk_bloom_device_bits(rsk_bloom *b);
 
+/* ------------------------------------------------------ Bloom filter pools */
+/* n_filters RBloomFilters of one (size, k) -- one dedup filter per tenant,
+ * user or shard, driven from an RBatch -- held as the rows of one bit string
+ * and added to / queried in ONE call, key i going to filter groups[i]
+ * (the grouped form of rsk_bloom_add / _contains, as rsk_hll_add_grouped is of
+ * rsk_hll_add).  Row r starts at bit r * stride_bits, stride_bits = size
+ * rounded up to a multiple of 32; the padding bits are never set.  Every
+ * result is what n_filters separate rsk_bloom handles would give. */
+typedef struct rsk_bloom_pool rsk_bloom_pool;
+/* Rows start zeroed.  n_filters >= 1, size >= 1, 1 <= k <= 4096 (else
+ * RSK_ERR_INVALID_ARG); RSK_ERR_OUT_OF_MEMORY when the rows do not fit. */
+int rsk_bloom_pool_create(rsk_ctx *ctx, uint64_t n_filters, int64_t size, int32_t k, rsk_bloom_pool **out);
+int rsk_bloom_pool_destroy(rsk_bloom_pool *p);
+/* Any of the output pointers may be NULL. */
+int rsk_bloom_pool_info(const rsk_bloom_pool *p, uint64_t *n_filters, int64_t *size, int32_t *k,
+                        uint64_t *stride_bits);
+/* add(obj) on filter groups[i] for the n keys in input order
+ * (RedissonBloomFilter.java:80-114 per filter).  groups: n uint32 in the keys'
+ * location.  added_out (may be NULL; in the keys' location): added_out[i] = 1
+ * iff one of the first k-1 SETBITs of key i found its bit clear, as if the n
+ * adds ran one by one in input order.  A group id >= n_filters anywhere in the
+ * batch fails the call with RSK_ERR_INVALID_ARG before any row changes and
+ * before any reply is written. */
+int rsk_bloom_pool_add(rsk_bloom_pool *p, const rsk_keys *keys, const uint32_t *groups, uint8_t *added_out);
+/* contains(obj) on filter groups[i]: 1 iff the first k-1 bits of that row are
+ * set.  out in the keys' location. */
+int rsk_bloom_pool_contains(rsk_bloom_pool *p, const rsk_keys *keys, const uint32_t *groups, uint8_t *out);
+/* BITCOUNT and count() (RedissonBloomFilter.java:188-199) of rows ids[0..n)
+ * (host array; NULL = rows 0..n-1) into the host arrays out. */
+int rsk_bloom_pool_bitcount(rsk_bloom_pool *p, const uint64_t *ids, uint64_t n, uint64_t *out);
+int rsk_bloom_pool_count(rsk_bloom_pool *p, const uint64_t *ids, uint64_t n, int32_t *out);
+/* Row id as the Redis string a single RBloomFilter of this (size, k) holds
+ * (ceil(size/8) bytes, host memory): it moves to and from an rsk_bloom
+ * (rsk_bloom_import_bits / _export_bits) unchanged.  Import replaces the row. */
+int rsk_bloom_pool_export_bits(rsk_bloom_pool *p, uint64_t id, uint8_t *buf, size_t cap, size_t *len);
+int rsk_bloom_pool_import_bits(rsk_bloom_pool *p, uint64_t id, const uint8_t *buf, size_t len);
+/* The rows in HBM: n_filters * stride_bits / 8 bytes, row r at byte
+ * r * stride_bits / 8 (NULL for a NULL handle). */
+void *rsk_bloom_pool_device_bits(rsk_bloom_pool *p);
+/* Every row zeroed. */
+int rsk_bloom_pool_clear(rsk_bloom_pool *p);
+
 /* --------------------------------------------------------------- RBitSet */
 /* A Redis string addressed as bits, MSB-first (bitops.c; the layout the
  * Bloom filter uses).  Each call replaces the command RedissonBitSet sends

@@ -13,7 +13,7 @@ from .codec import (ByteArrayCodec, JavaInteger, JavaLong, JsonJacksonCodec, Lon
 from .keys import KeyBatch  # noqa: F401
 
 __all__ = [
-    "Redisson", "Config", "RHyperLogLog", "RBloomFilter", "GroupedHyperLogLog", "KeyBatch", "Engine",
+    "Redisson", "Config", "RHyperLogLog", "RBloomFilter", "GroupedHyperLogLog", "GroupedBloomFilter", "KeyBatch", "Engine",
     "JsonJacksonCodec", "StringCodec", "LongCodec", "ByteArrayCodec", "JavaLong", "JavaInteger",
     "IllegalArgumentException", "IllegalStateException", "RedisException", "EngineError", "RedissonError", "Hash",
 ]
@@ -29,10 +29,10 @@ def __getattr__(name):
         from . import hyperloglog
 
         return getattr(hyperloglog, name)
-    if name == "RBloomFilter":
+    if name in ("RBloomFilter", "GroupedBloomFilter"):
         from . import bloom
 
-        return bloom.RBloomFilter
+        return getattr(bloom, name)
     if name == "Hash":
         from . import misc
 

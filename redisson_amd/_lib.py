@@ -146,6 +146,17 @@ SIGNATURES = {
     "rsk_bloom_import_bits": (ctypes.c_int, [_vp, _vp, _sz]),
     "rsk_bloom_or_bits": (ctypes.c_int, [_vp, _vp, _sz, _u32]),
     "rsk_bloom_device_bits": (_vp, [_vp]),
+    "rsk_bloom_pool_create": (ctypes.c_int, [_vp, _u64, _i64, _i32, _P(_vp)]),
+    "rsk_bloom_pool_destroy": (ctypes.c_int, [_vp]),
+    "rsk_bloom_pool_info": (ctypes.c_int, [_vp, _P(_u64), _P(_i64), _P(_i32), _P(_u64)]),
+    "rsk_bloom_pool_add": (ctypes.c_int, [_vp, _P(rsk_keys), _vp, _vp]),
+    "rsk_bloom_pool_contains": (ctypes.c_int, [_vp, _P(rsk_keys), _vp, _vp]),
+    "rsk_bloom_pool_bitcount": (ctypes.c_int, [_vp, _vp, _u64, _vp]),
+    "rsk_bloom_pool_count": (ctypes.c_int, [_vp, _vp, _u64, _vp]),
+    "rsk_bloom_pool_export_bits": (ctypes.c_int, [_vp, _u64, _vp, _sz, _P(_sz)]),
+    "rsk_bloom_pool_import_bits": (ctypes.c_int, [_vp, _u64, _vp, _sz]),
+    "rsk_bloom_pool_device_bits": (_vp, [_vp]),
+    "rsk_bloom_pool_clear": (ctypes.c_int, [_vp]),
     "rsk_bitset_create": (ctypes.c_int, [_vp, _P(_vp)]),
     "rsk_bitset_destroy": (ctypes.c_int, [_vp]),
     "rsk_bitset_strlen": (ctypes.c_int, [_vp, _P(_u64)]),

@@ -148,3 +148,95 @@ class RBloomFilter:
         n = ctypes.c_size_t()
         _lib.check(_lib.load().rsk_bloom_export_bits(b, buf.ctypes.data, buf.size, ctypes.byref(n)))
         return buf[: n.value].tobytes()
+
+
+class GroupedBloomFilter:
+    """A pool of n_filters equal RBloomFilters addressed by filter id (one
+    dedup filter per tenant / user / shard, the many-small-filters RBatch
+    pattern): one call adds to or queries all of them (rsk_bloom_pool_*).
+    Every reply, count and byte string is what n_filters separate RBloomFilters
+    of the same (expectedInsertions, falseProbability) would give."""
+
+    def __init__(self, engine, n_filters: int, expectedInsertions: int, falseProbability: float,
+                 extended: bool = False):
+        self.engine = engine
+        self.n = int(n_filters)
+        self.size, self.k = bloom_params(expectedInsertions, falseProbability, extended)
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().rsk_bloom_pool_create(engine.ctx, self.n, self.size, self.k, ctypes.byref(h)))
+        self.pool = h
+
+    def close(self):
+        if self.pool:
+            _lib.load().rsk_bloom_pool_destroy(self.pool)
+            self.pool = None
+
+    def getSize(self) -> int:
+        return self.size
+
+    def getHashIterations(self) -> int:
+        return self.k
+
+    @staticmethod
+    def _groups(groups):
+        """uint32 numpy array (host keys) or a DeviceBuffer of uint32 (device keys)."""
+        if hasattr(groups, "ptr"):
+            return groups, groups.ptr
+        groups = np.ascontiguousarray(groups, np.uint32)
+        return groups, groups.ctypes.data
+
+    def add(self, keys: KeyBatch, groups, replies: bool = True):
+        """Key i goes to filter groups[i].  Returns add()'s replies in input
+        order (a DeviceBuffer for device-resident keys), or None."""
+        groups, gp = self._groups(groups)
+        ks = keys.as_struct()
+        if not replies:
+            _lib.check(_lib.load().rsk_bloom_pool_add(self.pool, ctypes.byref(ks), gp, None), "SETBIT")
+            return None
+        buf, ptr = out_buffer(keys, keys.n, self.engine)
+        _lib.check(_lib.load().rsk_bloom_pool_add(self.pool, ctypes.byref(ks), gp, ptr), "SETBIT")
+        if keys.on_device:
+            return buf
+        return [bool(x) for x in buf[: keys.n]]
+
+    def contains(self, keys: KeyBatch, groups):
+        groups, gp = self._groups(groups)
+        ks = keys.as_struct()
+        buf, ptr = out_buffer(keys, keys.n, self.engine)
+        _lib.check(_lib.load().rsk_bloom_pool_contains(self.pool, ctypes.byref(ks), gp, ptr), "GETBIT")
+        if keys.on_device:
+            return buf
+        return [bool(x) for x in buf[: keys.n]]
+
+    def _per_row(self, fn, ids, dtype):
+        n = self.n if ids is None else len(ids)
+        out = np.zeros(max(1, n), dtype=dtype)
+        ip = None
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.uint64)
+            ip = ids.ctypes.data
+        _lib.check(fn(self.pool, ip, n, out.ctypes.data), "BITCOUNT")
+        return out[:n]
+
+    def count(self, ids=None) -> np.ndarray:
+        """count() of every filter (ids None) or of ids (int32 each)."""
+        return self._per_row(_lib.load().rsk_bloom_pool_count, ids, np.int32)
+
+    def bitcount(self, ids=None) -> np.ndarray:
+        return self._per_row(_lib.load().rsk_bloom_pool_bitcount, ids, np.uint64)
+
+    # -- one filter's Redis string (what RBloomFilter.toByteArray returns)
+    def toByteArray(self, id: int) -> bytes:
+        buf = np.zeros(max(1, (self.size + 7) // 8), dtype=np.uint8)
+        n = ctypes.c_size_t()
+        _lib.check(_lib.load().rsk_bloom_pool_export_bits(self.pool, int(id), buf.ctypes.data, buf.size,
+                                                          ctypes.byref(n)))
+        return buf[: n.value].tobytes()
+
+    def fromByteArray(self, id: int, data: bytes) -> None:
+        a = np.frombuffer(bytes(data), dtype=np.uint8)
+        _lib.check(_lib.load().rsk_bloom_pool_import_bits(self.pool, int(id), a.ctypes.data if a.size else None,
+                                                          a.size))
+
+    def clear(self) -> None:
+        _lib.check(_lib.load().rsk_bloom_pool_clear(self.pool))

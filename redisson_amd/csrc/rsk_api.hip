@@ -2753,6 +2753,254 @@ void* rsk_bloom_device_bits(rsk_bloom* b) {
 
 }  // extern "C"
 
+// ------------------------------------------------------------ Bloom pools
+// F equal filters as F rows of one bit string (rsk_bloom_pool.hip).  A call is
+// the single filter's call on rsk_bloom_pool::all with the batch's row ids in
+// DevKeys::groups; the ids are validated first (one reduction), so a bad id
+// fails the call before any row or reply changes.
+namespace {
+
+void check_pool(const rsk_bloom_pool* p) { need(p != nullptr, "bloom pool handle is NULL"); }
+
+void pool_check_groups(rsk_bloom_pool* p, const rsk_keys* keys, const uint32_t* groups) {
+  uint32_t mx = 0;
+  if (keys->location == RSK_MEM_HOST) {
+    for (uint64_t i = 0; i < keys->n; ++i) mx = std::max(mx, groups[i]);
+  } else {
+    mx = bloom_pool_max_group(p->all.ctx, groups, keys->n);
+  }
+  if ((uint64_t)mx >= p->n_filters)
+    fail(RSK_ERR_INVALID_ARG, "group id " + std::to_string(mx) + " out of range (the pool has " +
+                                  std::to_string(p->n_filters) + " filters)");
+}
+
+// fn(dk, d_out): dk carries the chunk's row ids; d_out (null without outputs)
+// is the chunk's per-key output on the device, read back for host batches.
+template <class F>
+void pool_for_each_chunk(rsk_bloom_pool* p, const rsk_keys* keys, const uint32_t* groups, uint8_t* out, F&& fn) {
+  rsk_ctx* c = p->all.ctx;
+  const bool host = keys->location == RSK_MEM_HOST;
+  for_each_chunk(c, keys, [&](const DevKeys& chunk, uint64_t first, uint64_t cnt) {
+    DevKeys dk = chunk;
+    dk.gstride = p->stride_bits;
+    uint8_t* d_out = nullptr;
+    if (host) {  // the chunk's ids go up with it, as the grouped PFADD's do
+      uint8_t* s = out_scratch(c, 4 * cnt + cnt);
+      auto* d_groups = reinterpret_cast<uint32_t*>(s);
+      RSK_HIP(hipMemcpyAsync(d_groups, groups + first, cnt * 4, hipMemcpyHostToDevice, c->stream));
+      dk.groups = d_groups;
+      if (out) d_out = s + 4 * cnt;
+    } else {
+      dk.groups = groups + first;
+      if (out) d_out = out + first;
+    }
+    fn(dk, d_out);
+    if (host && out) {
+      RSK_HIP(hipMemcpyAsync(out + first, d_out, cnt, hipMemcpyDeviceToHost, c->stream));
+      RSK_HIP(hipStreamSynchronize(c->stream));
+    }
+  });
+  RSK_HIP(hipStreamSynchronize(c->stream));
+}
+
+void check_pool_call(rsk_bloom_pool* p, const rsk_keys* keys, const uint32_t* groups, const uint8_t* out) {
+  rsk_ctx* c = p->all.ctx;
+  check_keys(c, keys);
+  need(keys->n == 0 || groups != nullptr, "groups is NULL");
+  if (keys->n == 0) return;
+  check_out(c, keys, groups);
+  check_out(c, keys, out);
+  pool_check_groups(p, keys, groups);
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsk_bloom_pool_create(rsk_ctx* c, uint64_t n_filters, int64_t size, int32_t k, rsk_bloom_pool** out) {
+  return guarded([&] {
+    need(out != nullptr, "NULL argument");
+    *out = nullptr;
+    need(c != nullptr, "ctx is NULL");
+    need(n_filters >= 1 && n_filters <= (1ull << 32), "n_filters must be in [1, 2^32]");
+    need(size > 0, "Bloom filter size must be > 0");
+    need(size <= BLOOM_EXT_MAX, "Bloom filter size exceeds device limit");
+    need(k >= 1 && k <= 4096, "hashIterations must be in [1, 4096]");
+    const uint64_t stride = ((uint64_t)size + 31) & ~31ull;
+    need(n_filters <= (uint64_t)BLOOM_EXT_MAX / stride, "Bloom pool size exceeds device limit");
+    CtxLock l(c);
+    *out = nullptr;
+    auto p = std::make_unique<rsk_bloom_pool>();
+    p->n_filters = n_filters;
+    p->size = size;
+    p->stride_bits = stride;
+    p->row_bytes = ((uint64_t)size + 7) / 8;
+    rsk_bloom& a = p->all;
+    a.ctx = c;
+    a.size = (int64_t)(n_filters * stride);
+    a.k = k;
+    a.nbytes = n_filters * stride / 8;
+    a.nwords = ((a.nbytes + 15) / 16) * 4;
+    a.fm = make_fastmod((uint64_t)size);  // a key's probes are taken mod its row's size
+    RSK_HIP(hipMalloc(&a.d_bits, a.nwords * 4));
+    hipError_t e = hipMemsetAsync(a.d_bits, 0, a.nwords * 4, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+      (void)hipFree(a.d_bits);
+      RSK_HIP(e);
+    }
+    *out = p.release();
+  });
+}
+
+int rsk_bloom_pool_destroy(rsk_bloom_pool* p) {
+  int rc = guarded([&] {
+    check_pool(p);
+    CtxLock l(p->all.ctx);
+    RSK_HIP(hipStreamSynchronize(p->all.ctx->stream));
+    RSK_HIP(hipFree(p->all.d_bits));
+  });
+  delete p;
+  return rc;
+}
+
+int rsk_bloom_pool_info(const rsk_bloom_pool* p, uint64_t* n_filters, int64_t* size, int32_t* k,
+                        uint64_t* stride_bits) {
+  return guarded([&] {
+    check_pool(p);
+    if (n_filters) *n_filters = p->n_filters;
+    if (size) *size = p->size;
+    if (k) *k = p->all.k;
+    if (stride_bits) *stride_bits = p->stride_bits;
+  });
+}
+
+int rsk_bloom_pool_add(rsk_bloom_pool* p, const rsk_keys* keys, const uint32_t* groups, uint8_t* added_out) {
+  return guarded([&] {
+    check_pool(p);
+    need(keys != nullptr, "keys is NULL");
+    rsk_ctx* c = p->all.ctx;
+    CtxLock l(c);
+    check_pool_call(p, keys, groups, added_out);
+    if (keys->n == 0) return;
+    pool_for_each_chunk(p, keys, groups, added_out, [&](const DevKeys& dk, uint8_t* d_out) {
+      if (d_out) bloom_add_replies_launch(c, &p->all, dk, d_out);
+      else bloom_add_launch(c, &p->all, dk);
+    });
+  });
+}
+
+int rsk_bloom_pool_contains(rsk_bloom_pool* p, const rsk_keys* keys, const uint32_t* groups, uint8_t* out) {
+  return guarded([&] {
+    check_pool(p);
+    need(keys != nullptr, "keys is NULL");
+    need(out != nullptr, "out is NULL");
+    rsk_ctx* c = p->all.ctx;
+    CtxLock l(c);
+    check_pool_call(p, keys, groups, out);
+    if (keys->n == 0) return;
+    pool_for_each_chunk(p, keys, groups, out,
+                        [&](const DevKeys& dk, uint8_t* d_out) { bloom_contains_launch(c, &p->all, dk, d_out); });
+  });
+}
+
+int rsk_bloom_pool_bitcount(rsk_bloom_pool* p, const uint64_t* ids, uint64_t n, uint64_t* out) {
+  return guarded([&] {
+    check_pool(p);
+    need(n == 0 || out != nullptr, "out is NULL");
+    if (ids) {
+      for (uint64_t i = 0; i < n; ++i) need(ids[i] < p->n_filters, "filter id out of range");
+    } else {
+      need(n <= p->n_filters, "more rows than the pool has filters");
+    }
+    if (n == 0) return;
+    rsk_ctx* c = p->all.ctx;
+    CtxLock l(c);
+    uint8_t* w = c->work(16 * n);
+    uint64_t* d_out = reinterpret_cast<uint64_t*>(w);
+    uint64_t* d_ids = nullptr;
+    if (ids) {
+      d_ids = reinterpret_cast<uint64_t*>(w + 8 * n);
+      RSK_HIP(hipMemcpyAsync(d_ids, ids, 8 * n, hipMemcpyHostToDevice, c->stream));
+    }
+    bloom_pool_bitcount_launch(c, p->all.d_bits, p->stride_bits / 32, p->row_bytes, d_ids, n, d_out);
+    RSK_HIP(hipMemcpyAsync(out, d_out, 8 * n, hipMemcpyDeviceToHost, c->stream));
+    RSK_HIP(hipStreamSynchronize(c->stream));
+  });
+}
+
+int rsk_bloom_pool_count(rsk_bloom_pool* p, const uint64_t* ids, uint64_t n, int32_t* out) {
+  std::vector<uint64_t> bc;
+  int rc = guarded([&] {
+    check_pool(p);
+    need(n == 0 || out != nullptr, "out is NULL");
+    need(n <= (1ull << 32), "too many rows");
+    bc.resize(n);
+  });
+  if (rc != RSK_OK) return rc;
+  rc = rsk_bloom_pool_bitcount(p, ids, n, bc.data());
+  if (rc != RSK_OK) return rc;
+  return guarded([&] {
+    for (uint64_t i = 0; i < n; ++i) {
+      // (int) (-size / ((double) k) * Math.log(1 - bitcount / ((double) size))), as rsk_bloom_count
+      volatile double a = (double)(-p->size) / (double)p->all.k;
+      volatile double q = (double)bc[i] / (double)p->size;
+      volatile double lg = std::log(1 - q);
+      out[i] = java_d2i(a * lg);
+    }
+  });
+}
+
+int rsk_bloom_pool_export_bits(rsk_bloom_pool* p, uint64_t id, uint8_t* buf, size_t cap, size_t* len) {
+  return guarded([&] {
+    check_pool(p);
+    need(len != nullptr, "NULL argument");
+    need(id < p->n_filters, "filter id out of range");
+    need(buf != nullptr && cap >= p->row_bytes, "buffer smaller than ceil(size/8)");
+    rsk_ctx* c = p->all.ctx;
+    CtxLock l(c);
+    const uint8_t* row = reinterpret_cast<const uint8_t*>(p->all.d_bits) + id * (p->stride_bits / 8);
+    RSK_HIP(hipMemcpyAsync(buf, row, p->row_bytes, hipMemcpyDeviceToHost, c->stream));
+    RSK_HIP(hipStreamSynchronize(c->stream));
+    *len = p->row_bytes;
+  });
+}
+
+int rsk_bloom_pool_import_bits(rsk_bloom_pool* p, uint64_t id, const uint8_t* buf, size_t len) {
+  return guarded([&] {
+    check_pool(p);
+    need(id < p->n_filters, "filter id out of range");
+    need(len <= p->row_bytes, "bit string longer than the filter");
+    need(buf != nullptr || len == 0, "buf is NULL");
+    rsk_ctx* c = p->all.ctx;
+    CtxLock l(c);
+    uint8_t* row = reinterpret_cast<uint8_t*>(p->all.d_bits) + id * (p->stride_bits / 8);
+    RSK_HIP(hipMemsetAsync(row, 0, p->stride_bits / 8, c->stream));  // SET replaces the whole string
+    if (len) RSK_HIP(hipMemcpyAsync(row, buf, len, hipMemcpyHostToDevice, c->stream));
+    RSK_HIP(hipStreamSynchronize(c->stream));
+  });
+}
+
+void* rsk_bloom_pool_device_bits(rsk_bloom_pool* p) {
+  if (!p) {
+    set_error("bloom pool handle is NULL");
+    return nullptr;
+  }
+  return p->all.d_bits;
+}
+
+int rsk_bloom_pool_clear(rsk_bloom_pool* p) {
+  return guarded([&] {
+    check_pool(p);
+    rsk_ctx* c = p->all.ctx;
+    CtxLock l(c);
+    RSK_HIP(hipMemsetAsync(p->all.d_bits, 0, p->all.nwords * 4, c->stream));
+    RSK_HIP(hipStreamSynchronize(c->stream));
+  });
+}
+
+}  // extern "C"
+
 // ------------------------------------------------------------ asynchronous
 namespace {
 

@@ -26,17 +26,18 @@ RSK_DEV void key_hashes(const uint8_t* __restrict__ data, const uint64_t* __rest
   bloom_key_hashes<FIXED16>(data, offsets, fixed_len, i, h1, h2);
 }
 
-template <bool FIXED16>
+template <bool FIXED16, class GEN = NoGroups>
 __global__ __launch_bounds__(256) void bloom_add_kernel(const uint8_t* __restrict__ data,
                                                         const uint64_t* __restrict__ offsets, uint32_t fixed_len,
                                                         uint64_t n, uint32_t* __restrict__ bits, FastMod63 fm,
-                                                        int k) {
+                                                        int k, GEN gen = GEN{}) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t h1, h2;
     key_hashes<FIXED16>(data, offsets, fixed_len, i, h1, h2);
     ProbeSeq ps(h1, h2, fm);
+    const uint64_t row = gen.base(i);
     for (int t = 0; t < k; ++t) {
-      atomicOr(&bits[ps.idx >> 5], bit_mask(ps.idx));
+      atomicOr(&bits[(row + ps.idx) >> 5], bit_mask(ps.idx));
       if (t + 1 < k) ps.next(t, fm);
     }
   }
@@ -50,8 +51,10 @@ static void launch_contains_ee(rsk_ctx* c, rsk_bloom* b, const DevKeys& k, uint8
   uint64_t cap = (uint64_t)c->num_cus * blocks_per_cu;
   if (g > cap) g = cap;
   if (g == 0) g = 1;
-  hipLaunchKernelGGL(bloom_contains16_ee_kernel<U>, dim3((uint32_t)g), dim3(256), 0, c->stream,
-                     reinterpret_cast<const uint4*>(k.data), k.n, b->d_bits, b->fm, b->k, d_out);
+  with_probe_gen(k, [&](auto gen) {
+    hipLaunchKernelGGL((bloom_contains16_ee_kernel<U, decltype(gen)>), dim3((uint32_t)g), dim3(256), 0, c->stream,
+                       reinterpret_cast<const uint4*>(k.data), k.n, b->d_bits, b->fm, b->k, d_out, gen);
+  });
 }
 
 static bool fixed16(const DevKeys& k) {
@@ -66,12 +69,15 @@ static uint32_t grid_for(rsk_ctx* c, uint64_t n) {
 // k random memory-side atomicOr per key (small batches).
 void bloom_add_direct_launch(rsk_ctx* c, rsk_bloom* b, const DevKeys& k) {
   if (k.n == 0) return;
-  if (fixed16(k))
-    hipLaunchKernelGGL(bloom_add_kernel<true>, dim3(grid_for(c, k.n)), dim3(256), 0, c->stream, k.data, nullptr, 16u,
-                       k.n, b->d_bits, b->fm, b->k);
-  else
-    hipLaunchKernelGGL(bloom_add_kernel<false>, dim3(grid_for(c, k.n)), dim3(256), 0, c->stream, k.data, k.offsets,
-                       k.fixed_len, k.n, b->d_bits, b->fm, b->k);
+  with_probe_gen(k, [&](auto gen) {
+    using GEN = decltype(gen);
+    if (fixed16(k))
+      hipLaunchKernelGGL((bloom_add_kernel<true, GEN>), dim3(grid_for(c, k.n)), dim3(256), 0, c->stream, k.data,
+                         nullptr, 16u, k.n, b->d_bits, b->fm, b->k, gen);
+    else
+      hipLaunchKernelGGL((bloom_add_kernel<false, GEN>), dim3(grid_for(c, k.n)), dim3(256), 0, c->stream, k.data,
+                         k.offsets, k.fixed_len, k.n, b->d_bits, b->fm, b->k, gen);
+  });
   RSK_CHECK_LAUNCH("bloom_add_direct");
 }
 
@@ -94,8 +100,10 @@ void bloom_contains_launch(rsk_ctx* c, rsk_bloom* b, const DevKeys& k, uint8_t* 
     RSK_CHECK_LAUNCH("bloom_contains16");
   } else {
     ProfScope ps(c, "bloom_contains");
-    hipLaunchKernelGGL(bloom_contains_kernel<false>, dim3(grid_for(c, k.n)), dim3(256), 0, c->stream, k.data,
-                       k.offsets, k.fixed_len, k.n, b->d_bits, b->fm, b->k, d_out);
+    with_probe_gen(k, [&](auto gen) {
+      hipLaunchKernelGGL((bloom_contains_kernel<false, decltype(gen)>), dim3(grid_for(c, k.n)), dim3(256), 0,
+                         c->stream, k.data, k.offsets, k.fixed_len, k.n, b->d_bits, b->fm, b->k, d_out, gen);
+    });
     RSK_CHECK_LAUNCH("bloom_contains");
   }
 }
@@ -104,16 +112,18 @@ void bloom_contains_launch(rsk_ctx* c, rsk_bloom* b, const DevKeys& k, uint8_t* 
 // Probe p = i*k + t.  A probe "finds its bit clear" iff the bit was clear
 // before the batch and p is the first probe (in sequence order) of that
 // bit.  Stable radix sort of (bit index, p) finds the first probe per bit.
+template <class GEN = NoGroups>
 __global__ void bloom_probe_kernel(const uint8_t* __restrict__ data, const uint64_t* __restrict__ offsets,
                                    uint32_t fixed_len, uint64_t n, const uint32_t* __restrict__ bits, FastMod63 fm,
                                    int k, uint64_t* __restrict__ pidx, uint32_t* __restrict__ pseq,
-                                   uint8_t* __restrict__ pclear) {
+                                   uint8_t* __restrict__ pclear, GEN gen = GEN{}) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t h1, h2;
     key_hashes<false>(data, offsets, fixed_len, i, h1, h2);
     ProbeSeq ps(h1, h2, fm);
+    const uint64_t row = gen.base(i);
     for (int t = 0; t < k; ++t) {
-      const uint64_t idx = ps.idx;
+      const uint64_t idx = row + ps.idx;
       if (t + 1 < k) ps.next(t, fm);
       uint64_t p = i * (uint64_t)k + t;
       pidx[p] = idx;
@@ -160,8 +170,10 @@ void bloom_add_each_launch(rsk_ctx* c, rsk_bloom* b, const DevKeys& k, uint8_t* 
   uint8_t* found0 = pclear + al(np);
   void* tmp = found0 + al(np);
   ProfScope ps(c, "bloom_add_each");
-  hipLaunchKernelGGL(bloom_probe_kernel, dim3(grid_for(c, n)), dim3(256), 0, c->stream, k.data, k.offsets, k.fixed_len,
-                     n, b->d_bits, b->fm, b->k, idx_in, seq_in, pclear);
+  with_probe_gen(k, [&](auto gen) {
+    hipLaunchKernelGGL(bloom_probe_kernel<decltype(gen)>, dim3(grid_for(c, n)), dim3(256), 0, c->stream, k.data,
+                       k.offsets, k.fixed_len, n, b->d_bits, b->fm, b->k, idx_in, seq_in, pclear, gen);
+  });
   RSK_CHECK_LAUNCH("bloom_probe");
   RSK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, idx_in, idx_out, seq_in, seq_out, (int)np, 0, end_bit,
                                              c->stream));
@@ -178,10 +190,7 @@ void bloom_add_each_launch(rsk_ctx* c, rsk_bloom* b, const DevKeys& k, uint8_t* 
 void bloom_add_replies_sorted(rsk_ctx* c, rsk_bloom* b, const DevKeys& k, uint8_t* d_out) {
   const uint64_t max_keys = std::max<uint64_t>(1, (1ull << 28) / (uint64_t)b->k);
   for (uint64_t done = 0; done < k.n; done += max_keys) {
-    DevKeys sub = k;
-    sub.n = std::min<uint64_t>(max_keys, k.n - done);
-    if (k.offsets) sub.offsets = k.offsets + done;
-    else sub.data = k.data + done * k.fixed_len;
+    const DevKeys sub = k.sub(done, std::min<uint64_t>(max_keys, k.n - done));
     bloom_add_each_launch(c, b, sub, d_out + done);
   }
 }

@@ -10,18 +10,20 @@ namespace rsk {
 namespace {
 
 // contains: AND of the first k-1 bits (the reference never reads idx_{k-1}).
-template <bool FIXED16>
+template <bool FIXED16, class GEN = NoGroups>
 __global__ __launch_bounds__(256) void bloom_contains_kernel(const uint8_t* __restrict__ data,
                                                              const uint64_t* __restrict__ offsets, uint32_t fixed_len,
                                                              uint64_t n, const uint32_t* __restrict__ bits,
-                                                             FastMod63 fm, int k, uint8_t* __restrict__ out) {
+                                                             FastMod63 fm, int k, uint8_t* __restrict__ out,
+                                                             GEN gen = GEN{}) {
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
     uint64_t h1, h2;
     bloom_key_hashes<FIXED16>(data, offsets, fixed_len, i, h1, h2);
     ProbeSeq ps(h1, h2, fm);
+    const uint64_t row = gen.base(i);
     uint32_t all = 1;
     for (int t = 0; t < k - 1; ++t) {
-      if ((bits[ps.idx >> 5] & bloom_bit_mask(ps.idx)) == 0) {  // first clear bit decides (early exit)
+      if ((bits[(row + ps.idx) >> 5] & bloom_bit_mask(ps.idx)) == 0) {  // first clear bit decides (early exit)
         all = 0;
         break;
       }
@@ -35,20 +37,23 @@ __global__ __launch_bounds__(256) void bloom_contains_kernel(const uint8_t* __re
 // a fresh key costs ~1/(1-fill) gathers instead of k-1 (fill ~0.52 at the
 // optimal size: ~2 instead of 6).  U keys per lane keep U dependent probe
 // chains in flight; the random 4-byte gather rate, not latency, is the bound.
-template <int U>
+template <int U, class GEN = NoGroups>
 __global__ __launch_bounds__(256) void bloom_contains16_ee_kernel(const uint4* __restrict__ keys, uint64_t n,
                                                                   const uint32_t* __restrict__ bits, FastMod63 fm,
-                                                                  int k, uint8_t* __restrict__ out) {
+                                                                  int k, uint8_t* __restrict__ out, GEN gen = GEN{}) {
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x * U;
   for (uint64_t base = ((uint64_t)blockIdx.x * blockDim.x) * U + threadIdx.x; base < n; base += stride) {
     ProbeSeq ps[U];
     bool alive[U];
+    uint64_t row[U];  // the key's row base (a pool; the constant 0 for a single filter), loaded with the key
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint64_t i = base + (uint64_t)u * blockDim.x;
       alive[u] = i < n;
+      row[u] = 0;
       if (alive[u]) {
         uint4 v = ld_nt16(keys + i);
+        row[u] = gen.base(i);
         uint64_t w0 = ((uint64_t)v.y << 32) | v.x, w1 = ((uint64_t)v.w << 32) | v.z;
         ps[u] = ProbeSeq(xxh64_16(w0, w1), farm_16(w0, w1), fm);
       }
@@ -62,7 +67,7 @@ __global__ __launch_bounds__(256) void bloom_contains16_ee_kernel(const uint4* _
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         idx[u] = ps[u].idx;
-        w[u] = alive[u] ? bits[idx[u] >> 5] : 0xFFFFFFFFu;
+        w[u] = alive[u] ? bits[(row[u] + idx[u]) >> 5] : 0xFFFFFFFFu;
       }
       bool any = false;
 #pragma unroll

@@ -62,22 +62,23 @@ constexpr int HIST_U = 4;  // 16-byte keys in flight per lane in hist
 constexpr int APPLY_T = 1024;
 constexpr int APPLY_U = 4;
 
+// row: the key's row base (GEN::base: a pool's row; 0 for a single filter)
 template <typename F>
-RSK_DEV void for_probes(uint64_t h1, uint64_t h2, int k, const FastMod63& fm, F&& f) {
+RSK_DEV void for_probes(uint64_t h1, uint64_t h2, int k, const FastMod63& fm, uint64_t row, F&& f) {
   ProbeSeq ps(h1, h2, fm);
   for (int t = 0; t < k; ++t) {
-    f(t, ps.idx);
+    f(t, row + ps.idx);
     if (t + 1 < k) ps.next(t, fm);
   }
 }
 
 // hist: cnt[s * G + b] = probes of block b's keys that land in slice s.
-template <bool FIXED16>
+template <bool FIXED16, class GEN = NoGroups>
 __global__ __launch_bounds__(HIST_T) void bloom_slice_hist_kernel(const uint8_t* __restrict__ data,
                                                                   const uint64_t* __restrict__ offsets,
                                                                   uint32_t fixed_len, uint64_t n, uint64_t per,
                                                                   FastMod63 fm, int k, uint32_t nslices,
-                                                                  uint32_t* __restrict__ cnt) {
+                                                                  uint32_t* __restrict__ cnt, GEN gen = GEN{}) {
   __shared__ uint32_t h[MAX_SLICES];
   for (uint32_t s = threadIdx.x; s < nslices; s += HIST_T) h[s] = 0;
   __syncthreads();
@@ -97,14 +98,14 @@ __global__ __launch_bounds__(HIST_T) void bloom_slice_hist_kernel(const uint8_t*
       for (int u = 0; u < HIST_U; ++u) {
         if (i + (uint64_t)u * HIST_T >= end) break;
         const uint64_t w0 = ((uint64_t)v[u].y << 32) | v[u].x, w1 = ((uint64_t)v[u].w << 32) | v[u].z;
-        for_probes(xxh64_16(w0, w1), farm_16(w0, w1), k, fm, count);
+        for_probes(xxh64_16(w0, w1), farm_16(w0, w1), k, fm, gen.base(i + (uint64_t)u * HIST_T), count);
       }
     }
   } else {
     for (uint64_t i = begin + threadIdx.x; i < end; i += HIST_T) {
       uint64_t h1, h2;
       bloom_key_hashes<false>(data, offsets, fixed_len, i, h1, h2);
-      for_probes(h1, h2, k, fm, count);
+      for_probes(h1, h2, k, fm, gen.base(i), count);
     }
   }
   __syncthreads();
@@ -146,13 +147,13 @@ __device__ __forceinline__ void tile_scatter(TileLds& L, uint32_t np, uint32_t* 
 
 // part1: block b's keys -> probes, partitioned by bin = idx >> shift1 (< 256);
 // bin's run of block b starts at start[bin * G + b].
-template <bool FIXED16>
+template <bool FIXED16, class GEN = NoGroups>
 __global__ __launch_bounds__(PT) void bloom_part1_kernel(const uint8_t* __restrict__ data,
                                                          const uint64_t* __restrict__ offsets, uint32_t fixed_len,
                                                          uint64_t n, uint64_t per, FastMod63 fm, int k,
                                                          uint32_t shift1, uint32_t nbins,
                                                          const uint32_t* __restrict__ start,
-                                                         uint32_t* __restrict__ out) {
+                                                         uint32_t* __restrict__ out, GEN gen = GEN{}) {
   __shared__ TileLds L;
   uint64_t begin, end;
   key_range(n, per, &begin, &end);
@@ -160,8 +161,8 @@ __global__ __launch_bounds__(PT) void bloom_part1_kernel(const uint8_t* __restri
   const uint64_t low = (1ull << shift1) - 1;
   L.hist[threadIdx.x] = 0;
   if (threadIdx.x < nbins) L.cur[threadIdx.x] = start[(uint64_t)threadIdx.x * gridDim.x + blockIdx.x];
-  auto hash_tile_key = [&](uint32_t q, uint64_t h1, uint64_t h2) {
-    for_probes(h1, h2, k, fm, [&](int t, uint64_t idx) {
+  auto hash_tile_key = [&](uint32_t q, uint64_t h1, uint64_t h2, uint64_t row) {
+    for_probes(h1, h2, k, fm, row, [&](int t, uint64_t idx) {
       const uint32_t b = (uint32_t)(idx >> shift1);
       const uint32_t r = atomicAdd(&L.hist[b], 1u);
       const uint32_t p = q * (uint32_t)k + (uint32_t)t;
@@ -192,7 +193,7 @@ __global__ __launch_bounds__(PT) void bloom_part1_kernel(const uint8_t* __restri
         const uint32_t q = threadIdx.x + u * PT;
         if (q < nk) {
           const uint64_t w0 = ((uint64_t)cur[u].y << 32) | cur[u].x, w1 = ((uint64_t)cur[u].w << 32) | cur[u].z;
-          hash_tile_key(q, xxh64_16(w0, w1), farm_16(w0, w1));
+          hash_tile_key(q, xxh64_16(w0, w1), farm_16(w0, w1), gen.base(k0 + q));
         }
       }
       tile_scatter(L, nk * (uint32_t)k, out);
@@ -204,7 +205,7 @@ __global__ __launch_bounds__(PT) void bloom_part1_kernel(const uint8_t* __restri
       for (uint32_t q = threadIdx.x; q < nk; q += PT) {
         uint64_t h1, h2;
         bloom_key_hashes<false>(data, offsets, fixed_len, k0 + q, h1, h2);
-        hash_tile_key(q, h1, h2);
+        hash_tile_key(q, h1, h2, gen.base(k0 + q));
       }
       tile_scatter(L, nk * (uint32_t)k, out);
     }
@@ -389,19 +390,19 @@ bool bloom_add_partitioned(rsk_ctx* c, rsk_bloom* b, const DevKeys& keys) {
   for (uint64_t first = 0; first < keys.n; first += chunk) {
     const uint64_t m = std::min<uint64_t>(chunk, keys.n - first);
     const uint64_t per = (m + G - 1) / G;
-    DevKeys dk = keys;
-    dk.n = m;
-    if (keys.offsets) dk.offsets = keys.offsets + first;
-    else dk.data = keys.data + first * keys.fixed_len;
+    const DevKeys dk = keys.sub(first, m);
     {
       ProfScope ps(c, "bloom_part_hist");
       RSK_HIP(hipMemsetAsync(cnt + ncnt - 1, 0, 4, c->stream));
-      if (f16)
-        hipLaunchKernelGGL(bloom_slice_hist_kernel<true>, dim3(G), dim3(HIST_T), 0, c->stream, dk.data, nullptr, 16u,
-                           m, per, b->fm, b->k, ns, cnt);
-      else
-        hipLaunchKernelGGL(bloom_slice_hist_kernel<false>, dim3(G), dim3(HIST_T), 0, c->stream, dk.data, dk.offsets,
-                           dk.fixed_len, m, per, b->fm, b->k, ns, cnt);
+      with_probe_gen(dk, [&](auto gen) {
+        using GEN = decltype(gen);
+        if (f16)
+          hipLaunchKernelGGL((bloom_slice_hist_kernel<true, GEN>), dim3(G), dim3(HIST_T), 0, c->stream, dk.data,
+                             nullptr, 16u, m, per, b->fm, b->k, ns, cnt, gen);
+        else
+          hipLaunchKernelGGL((bloom_slice_hist_kernel<false, GEN>), dim3(G), dim3(HIST_T), 0, c->stream, dk.data,
+                             dk.offsets, dk.fixed_len, m, per, b->fm, b->k, ns, cnt, gen);
+      });
       RSK_CHECK_LAUNCH("bloom_slice_hist");
       RSK_HIP(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, cnt, off2, (int)ncnt, c->stream));
       if (f2) {
@@ -413,12 +414,15 @@ bool bloom_add_partitioned(rsk_ctx* c, rsk_bloom* b, const DevKeys& keys) {
     {
       ProfScope ps(c, "bloom_part1");
       const uint32_t* start = f2 ? off1 : off2;
-      if (f16)
-        hipLaunchKernelGGL(bloom_part1_kernel<true>, dim3(G), dim3(PT), 0, c->stream, dk.data, nullptr, 16u, m, per,
-                           b->fm, b->k, shift1, nbins1, start, buf_a);
-      else
-        hipLaunchKernelGGL(bloom_part1_kernel<false>, dim3(G), dim3(PT), 0, c->stream, dk.data, dk.offsets,
-                           dk.fixed_len, m, per, b->fm, b->k, shift1, nbins1, start, buf_a);
+      with_probe_gen(dk, [&](auto gen) {
+        using GEN = decltype(gen);
+        if (f16)
+          hipLaunchKernelGGL((bloom_part1_kernel<true, GEN>), dim3(G), dim3(PT), 0, c->stream, dk.data, nullptr, 16u,
+                             m, per, b->fm, b->k, shift1, nbins1, start, buf_a, gen);
+        else
+          hipLaunchKernelGGL((bloom_part1_kernel<false, GEN>), dim3(G), dim3(PT), 0, c->stream, dk.data, dk.offsets,
+                             dk.fixed_len, m, per, b->fm, b->k, shift1, nbins1, start, buf_a, gen);
+      });
       RSK_CHECK_LAUNCH("bloom_part1");
     }
     if (f2) {

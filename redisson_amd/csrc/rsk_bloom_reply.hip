@@ -283,13 +283,14 @@ __global__ __launch_bounds__(TA_T) void rp_tapply_kernel(const uint32_t* __restr
 // [w S + g gs, min(w S + (g + 1) gs, (w + 1) S, nst)) of the chunk.
 RSK_DEV uint32_t hs_slot(uint64_t b) { return (uint32_t)((b * 0x9E3779B97F4A7C15ull) >> (64 - 10)); }
 
-template <bool FIXED16, int U>
+template <bool FIXED16, int U, class GEN = NoGroups>
 __global__ __launch_bounds__(RR_T) void rp_treply_kernel(const uint8_t* __restrict__ data,
                                                          const uint64_t* __restrict__ offsets, uint32_t fixed_len,
                                                          uint64_t m, FastMod63 fm, int k,
                                                          const uint16_t* __restrict__ T, uint8_t* __restrict__ out,
                                                          uint64_t kst, uint32_t S, uint32_t gs, uint32_t Gw,
-                                                         uint64_t nst, uint32_t* __restrict__ fallback) {
+                                                         uint64_t nst, uint32_t* __restrict__ fallback,
+                                                         GEN gen = GEN{}) {
   __shared__ uint32_t p_key[PEND_CAP], p_mask[PEND_CAP];
   __shared__ uint64_t hkey[HS];
   __shared__ uint32_t hmin[HS];
@@ -312,23 +313,26 @@ __global__ __launch_bounds__(RR_T) void rp_treply_kernel(const uint8_t* __restri
     ProbeSeq ps[U];
     bool live[U], open[U], yes[U];
     uint32_t pend[U];
+    uint64_t row[GEN::grouped ? U : 1];  // a pool: the key's row base (a single filter keeps none)
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const uint64_t i = base + (uint64_t)u * RR_T;
       live[u] = i < kb;
       yes[u] = false;
       pend[u] = 0;
+      if (GEN::grouped) row[u] = 0;
       if (live[u]) {
         uint64_t h1, h2;
         bloom_key_hashes<FIXED16>(data, offsets, fixed_len, i, h1, h2);
         ps[u] = ProbeSeq(h1, h2, fm);
+        if (GEN::grouped) row[u] = gen.base(i);
       }
       open[u] = live[u];
     }
     for (int t = 0; t < k - 1; ++t) {
       uint32_t v[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) v[u] = open[u] ? (uint32_t)T[ps[u].idx] : T_NONE;
+      for (int u = 0; u < U; ++u) v[u] = open[u] ? (uint32_t)T[(GEN::grouped ? row[u] : 0) + ps[u].idx] : T_NONE;
       bool any = false;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
@@ -380,17 +384,19 @@ __global__ __launch_bounds__(RR_T) void rp_treply_kernel(const uint8_t* __restri
   };
   for (uint32_t e = threadIdx.x; e < np; e += RR_T) {
     ProbeSeq ps = probes_of(ka + p_key[e]);
+    const uint64_t row = gen.base(ka + p_key[e]);
     const uint32_t mask = p_mask[e];
     for (int t = 0; t < k - 1; ++t) {
       if ((mask >> t) & 1u) {
-        uint32_t sl = hs_slot(ps.idx);
+        const uint64_t bit = row + ps.idx;
+        uint32_t sl = hs_slot(bit);
         for (uint32_t n = 0; n < HS; ++n) {
-          const uint64_t old = atomicCAS(reinterpret_cast<unsigned long long*>(&hkey[sl]), HS_EMPTY, ps.idx);
+          const uint64_t old = atomicCAS(reinterpret_cast<unsigned long long*>(&hkey[sl]), HS_EMPTY, bit);
           if (old == HS_EMPTY) {
             atomicAdd(&s_nh, 1u);
             break;
           }
-          if (old == ps.idx) break;
+          if (old == bit) break;
           sl = (sl + 1) & (HS - 1);
         }
       }
@@ -413,8 +419,9 @@ __global__ __launch_bounds__(RR_T) void rp_treply_kernel(const uint8_t* __restri
   };
   for (uint64_t j = ka + threadIdx.x; j < kb; j += RR_T) {
     ProbeSeq ps = probes_of(j);
+    const uint64_t row = gen.base(j);
     for (int t = 0; t < k; ++t) {
-      const uint32_t sl = lookup(ps.idx);
+      const uint32_t sl = lookup(row + ps.idx);
       if (sl < HS) atomicMin(&hmin[sl], ((uint32_t)(j - ka) << 4) | (uint32_t)t);
       if (t + 1 < k) ps.next(t, fm);
     }
@@ -422,10 +429,11 @@ __global__ __launch_bounds__(RR_T) void rp_treply_kernel(const uint8_t* __restri
   __syncthreads();
   for (uint32_t e = threadIdx.x; e < np; e += RR_T) {
     ProbeSeq ps = probes_of(ka + p_key[e]);
+    const uint64_t row = gen.base(ka + p_key[e]);
     const uint32_t mask = p_mask[e];
     bool y = false;
     for (int t = 0; t < k - 1; ++t) {
-      if ((mask >> t) & 1u) y |= hmin[lookup(ps.idx)] == ((p_key[e] << 4) | (uint32_t)t);
+      if ((mask >> t) & 1u) y |= hmin[lookup(row + ps.idx)] == ((p_key[e] << 4) | (uint32_t)t);
       if (t + 2 < k) ps.next(t, fm);
     }
     if (y) out[ka + p_key[e]] = 1;
@@ -562,10 +570,7 @@ bool bloom_add_replies_append(rsk_ctx* c, rsk_bloom* b, const DevKeys& keys, uin
     const uint32_t Wl = (uint32_t)((nst + S - 1) / S);
     const uint32_t Gw = std::min<uint32_t>(63, MAX_TAGS / Wl);
     const uint32_t gs = (S + Gw - 1) / Gw;
-    DevKeys dk = keys;
-    dk.n = m;
-    if (keys.offsets) dk.offsets = keys.offsets + first;
-    else dk.data = keys.data + first * keys.fixed_len;
+    const DevKeys dk = keys.sub(first, m);
     if ((uint64_t)gs * kst >= (1ull << 28)) {  // rp_treply packs (key - group start) << 4 | t in 32 bits
       bloom_add_replies_sorted(c, b, dk, d_out + first);
       continue;
@@ -574,15 +579,18 @@ bool bloom_add_replies_append(rsk_ctx* c, rsk_bloom* b, const DevKeys& keys, uin
     {
       ProfScope ps(c, "bloom_rp1");
 #define RSK_RP1(F16, KM, KPL, ...)                                                                                  \
-  hipLaunchKernelGGL((bloom_sa1_kernel<F16, KM, T1, uint32_t, KPL, true, ##__VA_ARGS__>), dim3(Wl), dim3(T1), 0,    \
+  hipLaunchKernelGGL((bloom_sa1_kernel<GEN, F16, KM, T1, uint32_t, KPL, true, ##__VA_ARGS__>), dim3(Wl), dim3(T1), 0, \
                      c->stream,                                                                                       \
                      dk.data, dk.offsets, dk.fixed_len, m, b->fm, b->k, shift1, nb1, nst, region, quota, limit, used, \
-                     flags, S, gs, c->tune.sa_full < 0 ? 2 : 0)
+                     flags, S, gs, c->tune.sa_full < 0 ? 2 : 0, gen)
+      with_probe_gen(dk, [&](auto gen) {
+      using GEN = decltype(gen);
       if (kpl4 && b->k == 7 && c->tune.sa_kc >= 0) RSK_RP1(true, 8, 4, 7);  // C3's k as a constant
       else if (kpl4) RSK_RP1(true, 8, 4);
       else if (f16) RSK_RP1(true, 16, 1);
       else if (kmax == 8) RSK_RP1(false, 8, 2);
       else RSK_RP1(false, 16, 1);
+      });
 #undef RSK_RP1
       RSK_CHECK_LAUNCH("bloom_rp1");
     }
@@ -639,13 +647,16 @@ bool bloom_add_replies_append(rsk_ctx* c, rsk_bloom* b, const DevKeys& keys, uin
       ProfScope ps(c, "bloom_rp_reply");
       const uint32_t ng = Wl * Gw;  // one workgroup per key group
 #define RSK_RPR(F16, U)                                                                                            \
-  hipLaunchKernelGGL((rp_treply_kernel<F16, U>), dim3(ng), dim3(RR_T), 0, c->stream, dk.data, dk.offsets,         \
-                     dk.fixed_len, m, b->fm, b->k, T, d_out + first, kst, S, gs, Gw, nst, flags + 1)
+  hipLaunchKernelGGL((rp_treply_kernel<F16, U, GEN>), dim3(ng), dim3(RR_T), 0, c->stream, dk.data, dk.offsets,    \
+                     dk.fixed_len, m, b->fm, b->k, T, d_out + first, kst, S, gs, Gw, nst, flags + 1, gen)
       const int u = c->tune.reply_u;  // gather chains per lane (default 2)
-      if (!f16) RSK_RPR(false, 2);
-      else if (u == 1) RSK_RPR(true, 1);
-      else if (u == 4) RSK_RPR(true, 4);
-      else RSK_RPR(true, 2);
+      with_probe_gen(dk, [&](auto gen) {
+        using GEN = decltype(gen);
+        if (!f16) RSK_RPR(false, 2);
+        else if (u == 1) RSK_RPR(true, 1);
+        else if (u == 4) RSK_RPR(true, 4);
+        else RSK_RPR(true, 2);
+      });
 #undef RSK_RPR
       RSK_CHECK_LAUNCH("bloom_rp_reply");
     }

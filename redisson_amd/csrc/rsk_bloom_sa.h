@@ -172,12 +172,16 @@ constexpr uint32_t SA2_SLOTS = SA2_T * SA2_V * 4;  // records per sa2h tile
 // sub-region (w, c) g never decreases, so key order is known per group.
 // HX (timing only, diag route sa_hash): 1 = the key words as h1 / h2 (no
 // hashes), 2 = also no mods (idx_0 = h1 mod 2^32) -- wrong filters.
-template <bool FIXED16, int KMAX, int T1, class R, int KPL = 16 / KMAX, bool TAGGED = false, int KC = 0, int HX = 0>
+// GEN: the probe generator (NoGroups: one filter; RowGroups: the rows of a
+// pool -- a key's row base is loaded where its probes are made and lives only
+// across them).
+template <class GEN, bool FIXED16, int KMAX, int T1, class R, int KPL = 16 / KMAX, bool TAGGED = false, int KC = 0,
+          int HX = 0>
 __global__ __launch_bounds__(T1, KPL * KMAX > 16 ? 4 : (T1 == 512 ? 6 : 4)) void bloom_sa1_kernel(
     const uint8_t* __restrict__ data, const uint64_t* __restrict__ offsets, uint32_t fixed_len, uint64_t n,
     FastMod63 fm, int k, uint32_t shift1, uint32_t nb1, uint64_t nst, R* __restrict__ region, uint32_t quota,
-    uint32_t limit, uint32_t* __restrict__ used, uint32_t* __restrict__ overflow, uint32_t S = 0, uint32_t gs = 1,
-    int dbg = 0) {
+    uint32_t limit, uint32_t* __restrict__ used, uint32_t* __restrict__ overflow, uint32_t S, uint32_t gs,
+    int dbg, GEN gen) {
   constexpr uint32_t KST = T1 * KPL;
   constexpr int NP = KPL * KMAX;
   const int kk = KC ? KC : k;  // KC: k known at compile time (the probe loop without the t < k tests)
@@ -281,13 +285,14 @@ __global__ __launch_bounds__(T1, KPL * KMAX > 16 ? 4 : (T1 == 512 ? 6 : 4)) void
         } else {
           ps = ProbeSeq(h1, h2, fm);
         }
+        const uint64_t row = ok ? gen.base(k0 + q) : 0;
 #pragma unroll
         for (int t = 0; t < KMAX; ++t) {
           const int s = u * KMAX + t;
           tag[s] = INVALID;
           pay[s] = 0;
           if (ok && t < kk) {
-            const uint64_t idx = ps.idx;
+            const uint64_t idx = row + ps.idx;
             const uint32_t bin = (uint32_t)(idx >> shift1);
             pay[s] = (R)((uint32_t)(idx & low) | gtag);
             tag[s] = (bin << 16) | atomicAdd(&hist[bin], 1u);

@@ -49,12 +49,13 @@ constexpr uint64_t DEFAULT_PROBE_CHUNK = 1ull << 33;   // probes per chunk (2 x 
 // out[st * KST * k ...], header hdr[st][0..nb1] (bin offsets, [nb1] = total).
 // The sorted image is double-buffered in LDS, so a tile's write-out overlaps
 // the next tile's hashing: three barriers per super-tile.
-template <bool FIXED16, int KMAX, int T1>
+// GEN: the probe generator (NoGroups: one filter; RowGroups: a pool's rows).
+template <bool FIXED16, int KMAX, int T1, class GEN = NoGroups>
 __global__ __launch_bounds__(T1) void bloom_st1_kernel(const uint8_t* __restrict__ data,
                                                        const uint64_t* __restrict__ offsets, uint32_t fixed_len,
                                                        uint64_t n, FastMod63 fm, int k, uint32_t shift1, uint32_t nb1,
                                                        uint64_t nst, uint32_t* __restrict__ out,
-                                                       uint16_t* __restrict__ hdr) {
+                                                       uint16_t* __restrict__ hdr, GEN gen = GEN{}) {
   constexpr int KPL = 16 / KMAX;        // keys per lane
   constexpr uint32_t KST = T1 * KPL;    // keys per super-tile
   constexpr int NP = KPL * KMAX;        // probe slots per lane (16)
@@ -99,13 +100,14 @@ __global__ __launch_bounds__(T1) void bloom_st1_kernel(const uint8_t* __restrict
         }
       }
       ProbeSeq ps(h1, h2, fm);
+      const uint64_t row = ok ? gen.base(k0 + q) : 0;
 #pragma unroll
       for (int t = 0; t < KMAX; ++t) {
         const int s = u * KMAX + t;
         tag[s] = INVALID;
         pay[s] = 0;
         if (ok && t < k) {
-          const uint64_t idx = ps.idx;
+          const uint64_t idx = row + ps.idx;
           const uint32_t bin = (uint32_t)(idx >> shift1);
           pay[s] = (uint32_t)(idx & low);
           tag[s] = (bin << 16) | atomicAdd(&hist[bin], 1u);
@@ -437,19 +439,18 @@ bool bloom_add_append(rsk_ctx* c, rsk_bloom* b, const DevKeys& keys, bool f16, u
     const uint64_t m = std::min<uint64_t>(chunk, keys.n - first);
     const uint64_t nst = (m + kst - 1) / kst;
     const uint32_t Wc = (uint32_t)std::min<uint64_t>(W, nst);
-    DevKeys dk = keys;
-    dk.n = m;
-    if (keys.offsets) dk.offsets = keys.offsets + first;
-    else dk.data = keys.data + first * keys.fixed_len;
+    const DevKeys dk = keys.sub(first, m);
     RSK_HIP(hipMemsetAsync(overflow, 0, 4, c->stream));
     // the timing-only contiguous form needs nst whole images in the region
     const int sa_dbg = c->tune.sa_dbg && nst * (kst * kmax + 1024) <= region_probes ? 1 : 0;
     {
       ProfScope ps(c, "bloom_st1");
-#define RSK_SA1(F16, KM, ...)                                                                                   \
-  hipLaunchKernelGGL((bloom_sa1_kernel<F16, KM, T1, uint32_t, ##__VA_ARGS__>), dim3(Wc), dim3(T1), 0, c->stream, \
-                     dk.data, dk.offsets, dk.fixed_len, m, b->fm, b->k, shift1, nb1, nst, region, quota, limit,  \
-                     used, overflow, 0u, 1u, sa_dbg | (c->tune.sa_full < 0 ? 2 : 0))
+#define RSK_SA1(F16, KM, ...)                                                                                     \
+  hipLaunchKernelGGL((bloom_sa1_kernel<GEN, F16, KM, T1, uint32_t, ##__VA_ARGS__>), dim3(Wc), dim3(T1), 0,        \
+                     c->stream, dk.data, dk.offsets, dk.fixed_len, m, b->fm, b->k, shift1, nb1, nst, region, quota, \
+                     limit, used, overflow, 0u, 1u, sa_dbg | (c->tune.sa_full < 0 ? 2 : 0), gen)
+      with_probe_gen(dk, [&](auto gen) {
+      using GEN = decltype(gen);
       if (kpl4 && b->k == 7 && c->tune.sa_hash == 1) RSK_SA1(true, 8, 4, false, 7, 1);  // timing only
       else if (kpl4 && b->k == 7 && c->tune.sa_hash == 2) RSK_SA1(true, 8, 4, false, 7, 2);  // timing only
       else if (kpl4 && b->k == 7 && c->tune.sa_kc >= 0) RSK_SA1(true, 8, 4, false, 7);  // C3's k (1 % FPP)
@@ -458,6 +459,7 @@ bool bloom_add_append(rsk_ctx* c, rsk_bloom* b, const DevKeys& keys, bool f16, u
       else if (f16) RSK_SA1(true, 16);
       else if (kmax == 8) RSK_SA1(false, 8);
       else RSK_SA1(false, 16);
+      });
 #undef RSK_SA1
       RSK_CHECK_LAUNCH("bloom_sa1");
     }
@@ -515,21 +517,21 @@ void bloom_add_one_level(rsk_ctx* c, rsk_bloom* b, const DevKeys& keys, bool f16
   for (uint64_t first = 0; first < keys.n; first += chunk) {
     const uint64_t m = std::min<uint64_t>(chunk, keys.n - first);
     const uint64_t nst = (m + kst - 1) / kst;
-    DevKeys dk = keys;
-    dk.n = m;
-    if (keys.offsets) dk.offsets = keys.offsets + first;
-    else dk.data = keys.data + first * keys.fixed_len;
+    const DevKeys dk = keys.sub(first, m);
     {
       ProfScope ps(c, "bloom_st1");
 #define RSK_ST1(F16, KM)                                                                                       \
-  launch_persistent((const void*)bloom_st1_kernel<F16, KM, T1>, T1, nst, c, [&](uint32_t grid) {            \
-    hipLaunchKernelGGL((bloom_st1_kernel<F16, KM, T1>), dim3(grid), dim3(T1), 0, c->stream, dk.data,         \
-                       dk.offsets, dk.fixed_len, m, b->fm, b->k, (uint32_t)SL_LOG, ns, nst, l1, h1);         \
+  launch_persistent((const void*)bloom_st1_kernel<F16, KM, T1, GEN>, T1, nst, c, [&](uint32_t grid) {        \
+    hipLaunchKernelGGL((bloom_st1_kernel<F16, KM, T1, GEN>), dim3(grid), dim3(T1), 0, c->stream, dk.data,     \
+                       dk.offsets, dk.fixed_len, m, b->fm, b->k, (uint32_t)SL_LOG, ns, nst, l1, h1, gen);      \
   })
-      if (f16 && kmax == 8) RSK_ST1(true, 8);
-      else if (f16) RSK_ST1(true, 16);
-      else if (kmax == 8) RSK_ST1(false, 8);
-      else RSK_ST1(false, 16);
+      with_probe_gen(dk, [&](auto gen) {
+        using GEN = decltype(gen);
+        if (f16 && kmax == 8) RSK_ST1(true, 8);
+        else if (f16) RSK_ST1(true, 16);
+        else if (kmax == 8) RSK_ST1(false, 8);
+        else RSK_ST1(false, 16);
+      });
 #undef RSK_ST1
       RSK_CHECK_LAUNCH("bloom_st1");
     }

@@ -466,6 +466,25 @@ RSK_DEV uint32_t bloom_bit_mask(uint64_t idx) {
   return 1u << ((uint32_t)((idx >> 3) & 3) * 8 + 7 - (uint32_t)(idx & 7));
 }
 
+// ------------------------------------------------------- probe generators
+// Where key i's probes land.  A single filter: at ProbeSeq's idx_t (NoGroups,
+// base 0 -- a kernel instantiated with it is the single-filter kernel).  A
+// pool of equal filters (rsk_bloom_pool): the pool is one bit string of rows
+// `stride` bits apart (a multiple of 32, so bloom_bit_mask holds at any row
+// base), and key i's probes are groups[i] * stride + idx_t (RowGroups).  The
+// generator is a template parameter of the Bloom kernels, never a run-time
+// branch in their loops.
+struct NoGroups {
+  static constexpr bool grouped = false;
+  RSK_DEV uint64_t base(uint64_t) const { return 0; }
+};
+struct RowGroups {
+  static constexpr bool grouped = true;
+  const uint32_t* g;
+  uint64_t stride;
+  RSK_DEV uint64_t base(uint64_t i) const { return (uint64_t)g[i] * stride; }
+};
+
 // ------------------------------------------------------- synthetic streams
 RSK_DEV uint64_t splitmix64(uint64_t x) {
   uint64_t z = x + 0x9E3779B97F4A7C15ULL;

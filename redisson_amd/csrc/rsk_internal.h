@@ -330,6 +330,20 @@ struct rsk_bloom {
   uint64_t wgen = 1, rgen = 1, set_len = 0;
 };
 
+// A pool of n_filters equal filters (size bits, k probes each): one Redis-layout
+// bit string of rows stride_bits apart (size rounded up to a multiple of 32; the
+// padding bits stay zero).  `all` is the whole pool seen as one filter of
+// n_filters * stride_bits bits whose probes come from the RowGroups generator
+// (DevKeys::groups): its fm is the ROW's (mod size), everything else (size,
+// nwords, d_bits) the pool's, so the single-filter launchers run on it.
+struct rsk_bloom_pool {
+  rsk_bloom all;
+  uint64_t n_filters = 0;
+  int64_t size = 0;          // bits per filter
+  uint64_t stride_bits = 0;
+  uint64_t row_bytes = 0;    // ceil(size/8): one filter's Redis string
+};
+
 namespace rsk {
 
 // ---- profiling helpers (rsk_api.hip)
@@ -350,7 +364,30 @@ struct DevKeys {
   const uint64_t* offsets;  // nullptr for fixed stride
   uint64_t n;
   uint32_t fixed_len;
+  // Bloom pools (rsk_bloom_pool): key i goes to row groups[i] of a bit string
+  // whose rows are gstride bits apart (the RowGroups probe generator); null
+  // for a single filter.  Device memory, like the keys.
+  const uint32_t* groups = nullptr;
+  uint64_t gstride = 0;
+  // keys [first, first + m) of this batch
+  DevKeys sub(uint64_t first, uint64_t m) const {
+    DevKeys s = *this;
+    s.n = m;
+    if (offsets) s.offsets = offsets + first;
+    else s.data = data + first * fixed_len;
+    if (groups) s.groups = groups + first;
+    return s;
+  }
 };
+
+// Calls f with the batch's probe generator (rsk_device.h): RowGroups for a
+// pool's batch, NoGroups for a single filter's.  f is a generic lambda that
+// launches kernel<..., decltype(gen)>(..., gen), so a launch site is written once.
+template <class F>
+inline void with_probe_gen(const DevKeys& k, F&& f) {
+  if (k.groups) f(RowGroups{k.groups, k.gstride});
+  else f(NoGroups{});
+}
 
 // ---- HLL launchers (rsk_hll.hip)
 // Adds keys into slabs and max-merges them into sketch `id`; sets *d_flag
@@ -473,6 +510,14 @@ void bloom_or_launch(rsk_ctx* c, uint32_t* d_bits, const uint8_t* d_src, uint64_
 // and dst 16-byte aligned, words any count).
 void or_rows_into_launch(rsk_ctx* c, uint32_t* d_dst, const uint32_t* d_src, uint32_t rows, uint64_t words,
                          uint64_t stride);
+
+// ---- Bloom pool launchers (rsk_bloom_pool.hip).  add / contains of a pool are
+// the single-filter launchers above on rsk_bloom_pool::all with DevKeys::groups set.
+// max of d_groups[0..n) (the one reduction that validates a batch); synchronises the stream.
+uint32_t bloom_pool_max_group(rsk_ctx* c, const uint32_t* d_groups, uint64_t n);
+// d_out[i] = BITCOUNT of row d_ids[i] (d_ids null: row i): its first row_bytes bytes.
+void bloom_pool_bitcount_launch(rsk_ctx* c, const uint32_t* d_bits, uint64_t stride_words, uint64_t row_bytes,
+                                const uint64_t* d_ids, uint64_t n, uint64_t* d_out);
 
 // ---- exchange plans (rsk_plan.hip, host only)
 void plan_owned_range(uint64_t n, uint64_t N, uint64_t r, uint64_t* first, uint64_t* count);
