@@ -165,6 +165,19 @@ int rsk_hll_add_each(rsk_hll *h, uint64_t id, const rsk_keys *keys, uint8_t *out
  * location as the keys).  Grouped COUNT DISTINCT (BASELINE config 5). */
 int rsk_hll_add_grouped(rsk_hll *h, const rsk_keys *keys, const uint32_t *groups);
 
+/* One PFADD per element, element i to sketch groups[i], in input order
+ * (an RBatch of RHyperLogLog.add over many keys).  out[i] = the reply of the
+ * i-th PFADD: 1 iff the key was missing or the element raised a register of
+ * groups[i] as the sketch stood after elements 0..i-1.  groups and out in the
+ * keys' location.  Afterwards the pool is what Redis holds after the n
+ * commands: a sketch exists iff it did or received an element, and only a
+ * sketch in which a register grew has its card cache invalidated and a kept
+ * SET string forgotten.  Unlike rsk_hll_add_grouped, which ignores a group id
+ * >= rsk_hll_size(h), this call refuses the whole batch for one
+ * (RSK_ERR_INVALID_ARG, nothing changed): a reply for a key that is not there
+ * has no meaning. */
+int rsk_hll_add_grouped_each(rsk_hll *h, const rsk_keys *keys, const uint32_t *groups, uint8_t *out);
+
 /* PFCOUNT id -- RedissonHyperLogLog.count/countAsync (:50-53,:78-81), for
  * n ids at once; out is a host array of n uint64.  Honours and refreshes the
  * per-key cardinality cache exactly like pfcountCommand. */

@@ -61,6 +61,8 @@ const char *rsk_diag_last_error(void);
  *                 leaves unwritten then corrupts a register: the tests' hole check)
  *   gpart_dbg     TIMING ONLY (the grouped add stops before its apply): bit 0 the fine-bin pass
  *                 stores each round's image contiguously, bit 1 no fine-bin count pass
+ *   geach_chunk   grouped PFADD with replies (rsk_hll_add_grouped_each): elements per sub-chunk
+ *                 (0 = default 2^26; values above 2^26 are capped there)
  *   reset         every route back to automatic
  * Every route but sa_dbg, sa_hash, gpart_dbg and reply_dbg gives bit-identical results; they differ in speed only. */
 int rsk_diag_set_route(rsk_ctx *ctx, const char *name, int64_t value);

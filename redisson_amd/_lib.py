@@ -110,6 +110,7 @@ SIGNATURES = {
     "rsk_hll_add": (ctypes.c_int, [_vp, _u64, _P(rsk_keys), _vp]),
     "rsk_hll_add_each": (ctypes.c_int, [_vp, _u64, _P(rsk_keys), _vp]),
     "rsk_hll_add_grouped": (ctypes.c_int, [_vp, _P(rsk_keys), _vp]),
+    "rsk_hll_add_grouped_each": (ctypes.c_int, [_vp, _P(rsk_keys), _vp, _vp]),
     "rsk_hll_count": (ctypes.c_int, [_vp, _vp, _u64, _vp]),
     "rsk_hll_count_union": (ctypes.c_int, [_vp, _vp, _u32, _vp]),
     "rsk_hll_count_union_batch": (ctypes.c_int, [_vp, _vp, _u32, _u64, _vp]),

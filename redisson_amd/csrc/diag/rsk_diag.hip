@@ -209,6 +209,7 @@ int rsk_diag_set_route(rsk_ctx* c, const char* name, int64_t value) {
     else if (k == "copy_nt") t.copy_nt = (int)value;
     else if (k == "io_pin") t.io_pin = (int)value;
     else if (k == "io_engine") t.io_engine = (int)value;
+    else if (k == "geach_chunk") t.geach_chunk = (uint64_t)value;
     else if (k == "reset") t = Tuning{};
     else throw RskError{RSK_ERR_INVALID_ARG, "unknown route: " + k};
   });

@@ -1647,6 +1647,71 @@ int rsk_hll_add_grouped(rsk_hll* h, const rsk_keys* keys, const uint32_t* groups
   });
 }
 
+// Grouped PFADD with replies (rsk_hll_geach.hip).  The batch's ids are
+// validated first (one reduction for device ids), so a bad id fails the call
+// before anything changes.  Sub-chunks of at most 2^26 elements (route
+// geach_chunk) compose sequentially: each lands in the registers before the
+// next starts.  The kernels invalidate the card cache and retire the
+// precomputed PFCOUNT of exactly the sketches in which a register grew and
+// list them; the host marks those as existing and forgets their kept SET
+// strings (a missing sketch's first element always raises a register, so the
+// list holds every sketch the batch created).
+int rsk_hll_add_grouped_each(rsk_hll* h, const rsk_keys* keys, const uint32_t* groups, uint8_t* out) {
+  return guarded([&] {
+    need(h != nullptr, "hll handle is NULL");
+    need(keys != nullptr, "keys is NULL");
+    need(keys->n == 0 || groups != nullptr, "groups is NULL");
+    need(keys->n == 0 || out != nullptr, "out is NULL");
+    rsk_ctx* c = h->ctx;
+    CtxLock l(c);
+    check_keys(c, keys);
+    if (keys->n == 0) return;
+    check_out(c, keys, groups);
+    check_out(c, keys, out);
+    const bool host = keys->location == RSK_MEM_HOST;
+    uint32_t mx = 0;
+    if (host) {
+      for (uint64_t i = 0; i < keys->n; ++i) mx = std::max(mx, groups[i]);
+    } else {
+      mx = bloom_pool_max_group(c, groups, keys->n);
+    }
+    if ((uint64_t)mx >= h->n)
+      fail(RSK_ERR_INVALID_ARG, "group id " + std::to_string(mx) + " out of range (the pool has " +
+                                    std::to_string(h->n) + " sketches)");
+    hll_materialize(h);
+    const uint64_t max_chunk = std::min<uint64_t>(c->tune.geach_chunk ? c->tune.geach_chunk : 1ull << 26, 1ull << 26);
+    std::vector<uint32_t> changed;
+    // One sub-chunk; then the host state of the sketches it changed.
+    auto sub_chunk = [&](const DevKeys& dk, const uint32_t* d_groups, uint8_t* d_out) {
+      changed.clear();
+      if (hll_add_grouped_each_launch(c, dk, d_groups, h->d_regs, h->n, h->d_card, h->d_pepoch, d_out, &changed))
+        h->zero = false;
+      for (uint32_t g : changed) {
+        h->exists[g] = 1;
+        hll_forget_import(h, g);
+      }
+    };
+    for_each_chunk(c, keys, [&](const DevKeys& chunk, uint64_t first, uint64_t cnt) {
+      const uint32_t* d_groups = groups + first;
+      uint8_t* d_out = out + first;
+      if (host) {  // the chunk's ids go up with it; its replies come back before the next chunk
+        uint8_t* s = out_scratch(c, 4 * cnt + cnt);
+        RSK_HIP(hipMemcpyAsync(s, groups + first, cnt * 4, hipMemcpyHostToDevice, c->stream));
+        d_groups = reinterpret_cast<const uint32_t*>(s);
+        d_out = s + 4 * cnt;
+      }
+      for (uint64_t done = 0; done < cnt; done += max_chunk) {
+        const uint64_t m = std::min<uint64_t>(max_chunk, cnt - done);
+        sub_chunk(chunk.sub(done, m), d_groups + done, d_out + done);
+      }
+      if (host) {
+        RSK_HIP(hipMemcpyAsync(out + first, d_out, cnt, hipMemcpyDeviceToHost, c->stream));
+        RSK_HIP(hipStreamSynchronize(c->stream));
+      }
+    });
+  });
+}
+
 int rsk_hll_count(rsk_hll* h, const uint64_t* ids, uint64_t n, uint64_t* out) {
   return guarded([&] {
     need(h != nullptr && out != nullptr, "NULL argument");

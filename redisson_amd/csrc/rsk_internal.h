@@ -84,6 +84,7 @@ struct Tuning {
   int route_vrank = 0;       // route_vranks (its owned sub-range; records of other owners dropped)
   int route_heavy = 0;       // routed add's heavy-group pre-combine: 0 auto (>= 2048 pairs, N > 1 or self exchange,
                              // >= 2^22 pairs), -1 never, > 0 on at any size with that many pairs per heavy group
+  uint64_t geach_chunk = 0;  // grouped PFADD with replies: elements per sub-chunk (0: 2^26)
 };
 
 // An asynchronous call (rsk_*_async): its host inputs are copied into the
@@ -483,6 +484,16 @@ uint64_t hll_heavy_select(rsk_ctx* c, const uint32_t* d_groups, uint64_t n, uint
 // write_all: every row written (zero rows for sketches without records).
 void hll_add_grouped_recs_launch(rsk_ctx* c, const uint2* d_recs, uint64_t n, uint8_t* d_regs, uint64_t G,
                                  bool pool_zero, bool write_all, PCount pc);
+// Grouped PFADD with per-element replies (rsk_hll_geach.hip): one sub-chunk of
+// at most 2^26 elements, element i to sketch d_groups[i] (every id < G: the
+// caller has validated them).  d_out[i] = the i-th PFADD's reply, registers
+// raised in place; a sketch in which a register grew has bit 63 of its card
+// word set and its precomputed PFCOUNT stamp cleared, and its id is appended
+// to *changed (each id once).  Returns the number of elements that survived
+// the filter; synchronises the stream.
+uint64_t hll_add_grouped_each_launch(rsk_ctx* c, const DevKeys& k, const uint32_t* d_groups, uint8_t* d_regs, uint64_t G,
+                                     uint64_t* d_card, uint32_t* d_pepoch, uint8_t* d_out,
+                                     std::vector<uint32_t>* changed);
 // Performs a pending lazy clear (rsk_api.hip).
 void hll_materialize(const rsk_hll* h);
 // The rows among ids[0..n) / [first, first + count) that a partial lazy clear

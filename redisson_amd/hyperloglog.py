@@ -174,6 +174,30 @@ class GroupedHyperLogLog:
         ks = keys.as_struct()
         _lib.check(_lib.load().rsk_hll_add_grouped(self.pool, ctypes.byref(ks), gp))
 
+    def addEach(self, keys: KeyBatch, groups, out=None):
+        """One PFADD per element in input order, element i to sketch groups[i]
+        (an RBatch of add() over many keys; rsk_hll_add_grouped_each): the n
+        replies.  Host keys: groups a uint32 array, returns a uint8 array (`out`
+        when it is a contiguous uint8 array of at least n entries).  Device
+        keys: groups and `out` are DeviceBuffers (one of n bytes is allocated
+        when out is None) and the replies stay in HBM.  A group id outside the
+        pool fails the whole call and changes nothing."""
+        n = keys.n
+        if keys.on_device:
+            if out is None:
+                out, _ = out_buffer(keys, n, self.engine)
+            gp, op = groups.ptr, out.ptr
+        else:
+            groups = np.ascontiguousarray(groups, np.uint32)
+            if groups.size < n:
+                raise ValueError("groups must hold one id per key")
+            if out is None or out.dtype != np.uint8 or out.size < n or not out.flags.c_contiguous:
+                out = np.zeros(max(n, 1), dtype=np.uint8)
+            gp, op = groups.ctypes.data, out.ctypes.data
+        ks = keys.as_struct()
+        _lib.check(_lib.load().rsk_hll_add_grouped_each(self.pool, ctypes.byref(ks), gp, op), "PFADD")
+        return out if keys.on_device else out[:n]
+
     def count(self, ids=None, out=None) -> np.ndarray:
         """PFCOUNT of every sketch (ids None) or of ids; `out` (uint64, reused
         across calls) receives the counts."""
